@@ -73,6 +73,13 @@ class PipeReader:
         verdict (a reaper thread collects the exit later)."""
         out, err = self.text()
         rc = self.proc.poll()
+        if rc is None and not out.strip():
+            # no report to take a verdict from: the child is exiting (the kernel closes its pipes a
+            # moment before it can be reaped), so its status is about to be there
+            try:
+                rc = self.proc.wait(1.0)
+            except subprocess.TimeoutExpired:
+                rc = None
         if rc is None:
             rc = report_rc(out)
             threading.Thread(target=self.proc.wait, daemon=True).start()

@@ -20,6 +20,13 @@ kind/kubectl on the box); every GPU-touching step runs for real on the
 MI355X.  Under ``torch.distributed.run`` each rank owns one GPU and starts that
 GPU's processes (gloo control channel); the node is the N GPUs of the job.
 
+A plain run (``--gpus N --steps K --warmup W``) warms up, times the K bring-ups
+and prints the line.  ``--full`` adds what is reported next to the headline:
+the other operand mode's bring-ups, the config-5 pod workload and the
+collective sweep after the last timed bring-up.  ``--dump-outputs DIR`` writes
+what the last timed bring-up computed as ``DIR/<name>.npy``
+(:func:`bring_up_outputs`).
+
 Reference number: no time-to-Ready is published; BASELINE.md gives <= ~600 s
 (10 min pod AGE, README.md:202-206) and 1 allocatable GPU per node.
 """
@@ -49,6 +56,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline (warm-up, the timed bring-ups, the line): the other --mode's bring-ups "
+                         "(--compare), the config-5 pod workload and the collective sweep after the last timed "
+                         "bring-up, and the sweep after a failed one")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed bring-up computed (allocatable GPUs, the "
+                         "validation steps' and the validator kernel steps' verdicts) as DIR/<name>.npy")
     ap.add_argument("--fake-gpu", action="store_true", help="CPU-only: synthetic sysfs, no GPU processes")
     ap.add_argument("--fake-gpu-procs", action="store_true",
                     help="CPU-only, but start stand-in validator processes through the rank launcher")
@@ -74,12 +88,12 @@ def parse():
                          "operand images' entry point; device-plugin health watcher on) - the headline - or as "
                          "threads of the bench process (the round-1/2 lower bound)")
     ap.add_argument("--compare", type=int, default=2,
-                    help="after the timed steps, this many bring-ups in the other --mode (reported, not timed)")
+                    help="--full: after the timed steps, this many bring-ups in the other --mode (reported, not timed)")
     ap.add_argument("--no-pod-workload", action="store_true",
-                    help="skip the config-5 pod workload after the last timed bring-up")
+                    help="--full: skip the config-5 pod workload after the last timed bring-up")
     ap.add_argument("--pod-gemm", type=int, default=4096, help="GEMM size of the pod workload's pods")
     ap.add_argument("--no-sweep", action="store_true",
-                    help="skip the collective sweep (RCCL all-reduce / all-gather / reduce-scatter, 8 B ... "
+                    help="--full: skip the collective sweep (RCCL all-reduce / all-gather / reduce-scatter, 8 B ... "
                          "--sweep-max-bytes, and every xGMI link on its own) after the last timed bring-up")
     ap.add_argument("--sweep-max-bytes", type=int, default=1 << 30)
     ap.add_argument("--settle-s", type=float, default=0.0,
@@ -249,6 +263,7 @@ class StallMeter:
 
 KFD_PROCS = "/sys/class/kfd/kfd/proc"
 _LAST_STOP: list[float] = []  # perf_counter when the previous bring-up's cluster stopped
+_SEEDED: list[str] = []  # the bring-ups of this run so far (one_bring_up seeds the kubelet's tick phase by their count)
 
 
 def settle_gpu(settle_s: float) -> dict | None:
@@ -475,6 +490,58 @@ def slow_steps(cps: list[dict], factor: float = 1.3) -> list[dict]:
     return out
 
 
+# --dump-outputs: the validation steps and the validator's kernel steps, in a
+# fixed order (an array's columns mean the same in every build)
+READY_STEPS = ("driver", "toolkit", "workload", "plugin", "complete")
+KERNEL_STEPS = ("hip", "vecadd", "gemm", "gemm_fp8", "gemm_fp4", "gemm_fp6", "gemm_mxfp4", "hbm", "mfma", "xgmi", "rccl",
+                "dmabuf", "peers")
+NUMERIC_LABELS = ("amd.com/gpu.count", "amd.com/gpu.memory", "amd.com/gpu.xgmi.links")
+
+
+def bring_up_outputs(alloc: int, labels: dict, ready: dict, ranks: list, plugin_devices) -> dict:
+    """What one bring-up computed, as the arrays ``--dump-outputs`` writes:
+    the node as the cluster's users then see it and the verdicts of every
+    check behind that.  The validator's operands are seeded (validator_main.cpp),
+    so these are the same from run to run; its rates and times, and error
+    magnitudes that depend on the order of float atomics, are measurements
+    and stay in the detail file.  -1: not run / not reported."""
+    def flag(x):
+        return -1.0 if x is None else float(bool(x))
+
+    def num(x):
+        try:
+            return float(x)
+        except (TypeError, ValueError):
+            return -1.0
+
+    by_rank = [{s.get("name"): s for s in r.get("steps", [])} for r in ranks]
+    return {
+        "allocatable_amd_com_gpu": [float(alloc)],
+        "validation_ready": [flag(ready.get(s)) for s in READY_STEPS],
+        "node_validated": [flag(labels.get("amd.com/gpu.validated") == "true")],
+        "node_labels": [num(labels.get(k)) for k in NUMERIC_LABELS],
+        # per validator rank (GPU): each kernel step's verdict (numerics, counter gate and floor together)
+        "workload_steps_ok": [[flag((st.get(n) or {}).get("ok")) for n in KERNEL_STEPS] for st in by_rank],
+        # ... and the element counts its device-side checks found wrong (vectorAdd, RCCL) and the HBM
+        # copy's checksum verdict
+        "workload_mismatches": [[num((st.get("vecadd") or {}).get("mismatches")),
+                                 num((st.get("rccl") or {}).get("mismatches")),
+                                 flag((st.get("hbm") or {}).get("checksum_match"))] for st in by_rank],
+        # GPUs the plugin validation's pods held through the device plugin (the kubelet's device manager);
+        # the pods' own reports can arrive after Ready, so they are not part of this
+        "plugin_devices": [float(len(plugin_devices or []))],
+    }
+
+
+def dump_outputs(path: str, outputs: dict) -> None:
+    """``<path>/<name>.npy`` (float64) per array of :func:`bring_up_outputs`."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, rows in outputs.items():
+        np.save(os.path.join(path, f"{name}.npy"), np.asarray(rows, dtype=np.float64))
+
+
 def one_bring_up(args, n_gpus: int, launcher, workdir: str, fake_gpu: bool, mode: str = "process",
                  pods: bool = False) -> dict:
     from amdgpu_operator.api.clusterpolicy import REFERENCE_SET_FLAGS, deep_merge, parse_set_flags
@@ -501,7 +568,15 @@ def one_bring_up(args, n_gpus: int, launcher, workdir: str, fake_gpu: bool, mode
     from amdgpu_operator.nodeenv import NodeEnv
 
     d = tempfile.mkdtemp(prefix="step-", dir=workdir)
-    agent_poll = NodeEnv.poll_s if args.agent_poll_s is None else args.agent_poll_s
+    # The simulated kubelet draws the phase of its node-status tick (and the tick's jitter) from the
+    # `random` module: up to --kubelet-status-s of a bring-up's wall time, the larger part of ms_per_step.
+    # Seeded by the bring-up's number in this run, two runs with the same arguments wait through the same
+    # phases and their ms_per_step can be compared; time-to-Ready does not wait for the tick.
+    import random
+
+    random.seed(len(_SEEDED))
+    _SEEDED.append(d)
+    agent_poll =NodeEnv.poll_s if args.agent_poll_s is None else args.agent_poll_s
     # termination_s=0: kubelet-confirmed pod deletes, as on a cluster
     cluster = SimCluster(d, [node], fake_gpu=fake_gpu, poll_s=0.005, launcher=launcher, agent_poll_s=agent_poll,
                          node_status_s=args.kubelet_status_s or None, termination_s=0.0,
@@ -610,8 +685,12 @@ def one_bring_up(args, n_gpus: int, launcher, workdir: str, fake_gpu: bool, mode
                                  "main_at": main_at,
                                  "done_at": round(main_at + rep["seconds"], 4) if main_at is not None
                                  and isinstance(rep.get("seconds"), (int, float)) else None})
+        outputs = bring_up_outputs(
+            alloc, nobj["metadata"].get("labels") or {}, {s: s in timeline for s in READY_STEPS}, ranks,
+            plug.get("devices"))
         return {
             "mode": mode,
+            "outputs": outputs,
             "t0_wall": t0_wall,
             "settle": settle,
             "pod_workload": pod_workload,
@@ -1120,7 +1199,7 @@ def main():
         label = "timed" if out is results else "warm-up" if out is warm else "compare"
         try:
             for i in range(n_steps):
-                pods = out is results and i == n_steps - 1 and not args.no_pod_workload
+                pods = args.full and out is results and i == n_steps - 1 and not args.no_pod_workload
                 out.append(one_bring_up(args, n_gpus, launcher, workdir, fake_gpu, mode, pods))
                 # progress on stderr: a run that prints nothing for minutes looks hung to its
                 # caller, and every line also takes room from the JSON line in the driver's tail
@@ -1134,7 +1213,7 @@ def main():
                 err.update(records=e.records, elapsed_s=round(e.elapsed_s, 4), harness=getattr(e, "partial", None))
             print(f"bench: {label} bring-up {i + 1} failed: {type(e).__name__}: {str(e)[:200]}", file=sys.stderr,
                   flush=True)
-            if not args.no_sweep:
+            if args.full and not args.no_sweep:
                 # what the fabric does, measured, next to the failure (the floors it failed are in the records)
                 try:
                     err["collectives"] = standalone_sweep(args, launcher, fake_gpu, workdir)
@@ -1182,10 +1261,12 @@ def main():
     t1 = time.perf_counter()
     elapsed = t1 - t0
     kfd_held = holds_kfd()  # after the timed bring-ups, before the other-mode comparison
+    if args.dump_outputs and rank == 0 and results:
+        dump_outputs(args.dump_outputs, results[-1]["outputs"])
     # the other mode, untimed: in-process (lower bound) next to per-process
     other = "thread" if args.mode == "process" else "process"
     compare: list = []
-    do_compare = [args.compare > 0 and not errors]
+    do_compare = [args.full and args.compare > 0 and not errors]
     if world > 1:
         dist.broadcast_object_list(do_compare, src=0)  # every rank takes part in the launcher's loop, or none
     if do_compare[0]:

@@ -37,6 +37,40 @@ def pytest_collection_modifyitems(config, items):
             item.add_marker(skip)
 
 
+# A unix socket's path holds 107 bytes (sockaddr_un), and the tests put the
+# kubelet's and the plugins' sockets a few directories below tmp_path
+# (.../var/lib/kubelet/device-plugins/kubelet.sock).  That fits under
+# /tmp/pytest-of-<user>/pytest-<n>/<test>, but not when TMPDIR is a deep
+# directory (a CI workspace, a long home): there bind() fails with "AF_UNIX
+# path too long".  tmp_path is then a short directory of its own.
+_TMP_PATH_BUDGET = 60  # /tmp/pytest-of-root/pytest-0/ plus pytest's 30-character test directory name
+
+
+@pytest.fixture
+def tmp_path(tmp_path):
+    if len(str(tmp_path)) <= _TMP_PATH_BUDGET:
+        yield tmp_path
+        return
+    import pathlib
+    import shutil
+    import tempfile
+
+    short = None
+    for base in ("/tmp", "/var/tmp"):
+        try:
+            short = tempfile.mkdtemp(prefix="t", dir=base)
+            break
+        except OSError:
+            continue
+    if short is None:
+        yield tmp_path  # nowhere shorter to go
+        return
+    try:
+        yield pathlib.Path(short)
+    finally:
+        shutil.rmtree(short, ignore_errors=True)
+
+
 # threads of a gRPC server (rpc/wire.py ``<name>-accept``) or of a device
 # plugin's kubelet watch that a test started must be gone when it ends: a
 # leaked plugin re-registers with whatever kubelet socket appears later (and

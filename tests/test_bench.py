@@ -31,8 +31,8 @@ def _line(stdout: str) -> str:
 
 def test_bench_json_line_contract(tmp_path):
     detail = str(tmp_path / "detail.json")
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--fake-gpu", "--detail", detail],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--fake-gpu", "--full",
+                        "--detail", detail], cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.strip()]
     assert len(lines) == 1
@@ -76,6 +76,51 @@ def test_bench_json_line_contract(tmp_path):
     assert all(set(h) == {"start", "ready"} for h in d["kfd_holders"])
 
 
+def test_plain_run_is_the_headline_only_and_dumps_its_outputs(tmp_path):
+    """Without --full: warm-up, the timed bring-ups and the line - no other-mode
+    bring-ups, pod workload or collective sweep.  --dump-outputs writes the
+    last timed bring-up's results as float64 arrays."""
+    import numpy as np
+
+    detail, dump = str(tmp_path / "detail.json"), str(tmp_path / "out")
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--fake-gpu",
+                        "--detail", detail, "--dump-outputs", dump], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    out = json.loads(_line(p.stdout))
+    assert KEYS <= set(out) and list(out)[:len(HEAD)] == HEAD
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["unit"] == "s" and out["higher_is_better"] is False
+    assert 0 < out["value"] < 60 and out["ms_per_step"] >= out["value"] * 1000 and out["dtype"] == "bf16"
+    cfg = out["config"]
+    assert len(cfg["time_to_ready_s"]) == 2 and cfg["allocatable_amd_com_gpu"] == 1
+    assert not {"other_mode_time_to_ready_s", "pod_workload", "collectives"} & set(cfg)
+    with open(detail) as f:
+        d = json.load(f)
+    assert len(d["steps"]) == 2 and len(d["warmup"]) == 1 and d["compare"] == []
+    assert d["collectives"] is None and d["pod_workload"] is None
+    # the kubelet's node-status tick phase is seeded by the bring-up's number in the run (warm-up: 0), so
+    # the wait for allocatable - most of ms_per_step - is the same from run to run
+    import random
+
+    for i, step in enumerate(d["steps"], start=1):
+        random.seed(i)
+        phase = random.uniform(0, 10.0)  # --kubelet-status-s
+        late = step["allocatable_visible_s"] - phase  # less the cluster's start before the clock
+        # the first tick, or on a slow machine (Ready after it) the next one, a period + <= 4 % jitter later
+        assert -1.0 < late < 1.0 or 9.0 < late < 11.4, (i, phase, step["allocatable_visible_s"])
+    arrays ={n[:-4]: np.load(os.path.join(dump, n)) for n in sorted(os.listdir(dump))}
+    assert set(arrays) == {"allocatable_amd_com_gpu", "validation_ready", "node_validated", "node_labels",
+                           "workload_steps_ok", "workload_mismatches", "plugin_devices"}
+    assert all(a.dtype == np.float64 and a.size > 0 for a in arrays.values())
+    b = _bench()
+    assert arrays["allocatable_amd_com_gpu"].tolist() == [1.0] and arrays["node_validated"].tolist() == [1.0]
+    assert arrays["validation_ready"].tolist() == [1.0] * len(b.READY_STEPS)
+    assert arrays["node_labels"][0] == 1.0  # amd.com/gpu.count
+    ok = arrays["workload_steps_ok"]
+    assert ok.shape == (1, len(b.KERNEL_STEPS)) and set(ok.ravel().tolist()) <= {1.0, -1.0}
+    assert ok[0, b.KERNEL_STEPS.index("gemm")] == 1.0 and ok[0, b.KERNEL_STEPS.index("vecadd")] == 1.0
+    assert arrays["plugin_devices"].tolist() == [1.0]
+
+
 def test_bench_floor_failure_prints_a_structured_line(tmp_path):
     """A bring-up that fails its floors (here the RCCL busBW fraction set 250x
     above the link model) ends at once with the JSON line: value null, the
@@ -85,7 +130,7 @@ def test_bench_floor_failure_prints_a_structured_line(tmp_path):
     detail = str(tmp_path / "detail.json")
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
                         "--master-addr", "127.0.0.1", "--master-port=29617", "bench.py", "--gpus", "8", "--steps", "20",
-                        "--warmup", "0", "--fake-gpu-procs", "--compare", "0", "--detail", detail,
+                        "--warmup", "0", "--fake-gpu-procs", "--full", "--compare", "0", "--detail", detail,
                         "--set", "validator.workload.rcclBusbwLinkFraction=50"],
                        cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert p.returncode != 0
@@ -156,7 +201,7 @@ def test_bench_harness_never_opens_the_gpu():
     procs = "/sys/class/kfd/kfd/proc"
     if not os.path.isdir(procs):
         pytest.skip("no KFD process list in this container")
-    p = subprocess.Popen([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--compare", "0",
+    p = subprocess.Popen([sys.executable, "bench.py", "--steps", "1", "--warmup", "0", "--full", "--compare", "0",
                           "--detail", "gpurun_out/test_bench_detail.json"],
                          cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
     seen: set[str] = set()

@@ -28,7 +28,8 @@ def test_bench_ranks_with_stand_in_validators(nproc, warmup, port, mode, tmp_pat
     hand-over between phases; thread mode routes every GPU process through
     the rank that owns the GPU, process mode runs the operands as processes."""
     p = _torchrun(nproc, "bench.py", "--gpus", str(nproc), "--steps", "1", "--warmup", str(warmup),
-                  "--fake-gpu-procs", "--mode", mode, "--compare", "1", "--detail", str(tmp_path / "detail.json"), port=port)
+                  "--fake-gpu-procs", "--mode", mode, "--full", "--compare", "1", "--detail", str(tmp_path / "detail.json"),
+                  port=port)
     assert p.returncode == 0, p.stderr[-3000:]
     import json
 
@@ -77,7 +78,7 @@ def test_bench_n8_stays_within_the_gpu_process_budget(tmp_path):
     env = dict(os.environ, AMDGPU_FAKE_GPU_PROC_LOG=log_dir)
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=8",
                         "--master-addr", "127.0.0.1", "--master-port=29615", "bench.py", "--gpus", "8", "--steps", "1",
-                        "--warmup", "0", "--fake-gpu-procs", "--mode", "process", "--compare", "0",
+                        "--warmup", "0", "--fake-gpu-procs", "--mode", "process", "--full", "--compare", "0",
                         "--detail", str(tmp_path / "detail.json")],
                        capture_output=True, text=True, timeout=240, cwd=os.path.dirname(HERE), env=env)
     assert p.returncode == 0, p.stderr[-3000:]
